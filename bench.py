@@ -2,7 +2,9 @@
 """Headline benchmark: InfoDiffusion CelebA 64x64 training throughput (images/s) on
 N MI355X, one process per GPU, data-parallel over RCCL.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5                  # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full           # + every supplementary measurement below
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +12,15 @@ One step = `InfoDiff.loss_fn` (q_sample + encoder + AdaGN UNet + eps-MSE + recon
 forward, backward, gradient all-reduce (N > 1), clip_grad_norm_(1.0), AdamW --
 BASELINE.json configs[1]: CelebA 3x64x64, a_dim 32, mmd_weight 0.1, B = 32 per GPU,
 T = 1000, dropout 0.1, bf16 activations.  Random-pixel batches resident in HBM.
-Prints ONE JSON line (rank 0).  Extra keys: `roofline` (dominant kernel, HIP-event
-timed), `cpu_baseline` (the CPU oracle on the host cores, rank 0 at N = 1),
-`sampling` (DDIM-100 images/s, N = 1 only, --sampling).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line.
+--full adds what takes runs of its own, each with a --no-... switch: `roofline*` (dominant kernels, HIP-event
+timed), `sampling` (DDIM-100 images/s), `large_batch` / `fp32_value` / `atomics_value`, `dp_one_rank` and
+`dp_timeline` (the data-parallel step), `cpu_baseline` (the CPU oracle on the host cores, rank 0 at N = 1),
+`parity` (the recorded parity figures).
+--dump-outputs DIR writes what the last timed step handed back as DIR/<name>.npy (float32): `loss`,
+`grad_norm`, and one fixed, seeded sample each of the updated parameters (`params`) and of the clipped
+gradients the step left in `.grad` (`grads`).  Weights, batches and draws are seeded: the same arguments
+give the same arrays, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -38,6 +46,9 @@ def parse():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--graph', type=int, default=1, help='replay the step from a captured hipGraph')
     ap.add_argument('--fused-opt', type=int, default=1, help='fused clip+AdamW kernel (0: clip_grad_norm_ + torch AdamW)')
+    ap.add_argument('--full', action='store_true', help='also run the supplementary measurements (rooflines, DDIM-100 sampling, '
+                    'B=128 / fp32 / atomics steps, data-parallel probe and timeline, CPU baseline, recorded parity); each has a --no-... switch')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--sampling', action='store_true', help='(default now) also time DDIM-100 sampling (B=256)')
@@ -46,7 +57,10 @@ def parse():
     ap.add_argument('--no-large-batch', action='store_true', help='skip the supplementary B=128 training rate')
     ap.add_argument('--no-dp-probe', action='store_true', help='skip the one-rank data-parallel step (child process, IDF_FORCE_SYNC=1)')
     ap.add_argument('--cpu-baseline-worker', default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return a
 
 
 def make_args(a):
@@ -233,7 +247,7 @@ def one_rank_dp_cost(a):
     env['IDF_FORCE_SYNC'] = '1'
     env.setdefault('MASTER_PORT', '29547')
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(a.steps), '--warmup', str(a.warmup),
-           '--no-roofline', '--no-sampling', '--no-large-batch', '--no-cpu-baseline', '--no-dp-probe',
+           '--full', '--no-roofline', '--no-sampling', '--no-large-batch', '--no-cpu-baseline', '--no-dp-probe',
            '--batch', str(a.batch), '--a_dim', str(a.a_dim), '--dtype', a.dtype, '--graph', str(int(a.graph)),
            '--fused-opt', str(int(a.fused_opt))]
     try:
@@ -600,6 +614,31 @@ def large_batch_rate(a, margs, dev, batch=128, steps=10):
             'ms_per_step': round(dt / steps * 1e3, 3), 'steps': steps, 'note': 'supplementary; value above is B=32'}
 
 
+DUMP_SAMPLE = 4 << 20      # elements kept of each large output (16 MB as float32)
+
+
+def dump_outputs(path, loss, gnorm, model):
+    """--dump-outputs: what the caller of the timed step holds after its last call -- the loss it returned, the gradient norm
+    the optimizer reports, the updated parameters and the (clipped) gradients left in `.grad`, the last two as the same
+    seeded sample of their concatenation in parameter order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for p in model.parameters() if p.grad is not None]
+    with torch.no_grad():
+        flat = {'params': torch.cat([p.detach().float().reshape(-1) for p in params]),
+                'grads': torch.cat([p.grad.detach().float().reshape(-1) for p in params])}
+    n = flat['params'].numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(64).integers(0, n, DUMP_SAMPLE))).to(flat['params'].device)
+        flat = {k: v[idx] for k, v in flat.items()}
+    out = {k: v.cpu().numpy() for k, v in flat.items()}
+    out['loss'] = np.asarray([float(loss)], dtype=np.float32)
+    if gnorm is not None:
+        out['grad_norm'] = np.asarray([gnorm], dtype=np.float32)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + '.npy'), v.astype(np.float32, copy=False))
+
+
 def main():
     a = parse()
     if a.cpu_baseline_worker:
@@ -657,7 +696,7 @@ def main():
     trainer = GraphedTrainStep(model, margs, opt, sync=sync, use_graph=bool(a.graph), pre_step=pre)
 
     def step(i):
-        trainer(pool[i % 8], 0)
+        return trainer(pool[i % 8], 0)
 
     for i in range(max(4, a.warmup)):      # eager warm-up, capture (if any), first replay
         step(i)
@@ -673,7 +712,7 @@ def main():
     t0 = time.time()
     marks[0].record()
     for i in range(a.steps):
-        step(i)
+        loss = step(i)
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -689,6 +728,8 @@ def main():
     gnorm = float(opt.total_norm()) if a.fused_opt else None
     if gnorm is not None and not (gnorm == gnorm and gnorm < 1e6):
         raise RuntimeError('bench: non-finite gradient norm %r in the timed training step' % gnorm)
+    if a.dump_outputs and rank == 0:        # before anything below steps or differentiates the model again
+        dump_outputs(a.dump_outputs, loss, gnorm, model)
     imgs = a.batch * world * a.steps
     out = {
         'metric': 'training images/sec, CelebA 64x64 (InfoDiff loss_fn fwd+bwd+clip+AdamW)',
@@ -708,13 +749,14 @@ def main():
                    'last_grad_norm': None if gnorm is None else round(gnorm, 4)},
     }
 
-    par = parity_file()
+    par = parity_file() if a.full else None
     if par is not None:
         out['parity'] = par
     if sync is not None:
         out['ranks_seen'] = dist.get_world_size()       # after RCCL init: the ranks that actually take part in the exchange
-        out['dp_timeline'] = dp_timeline(trainer, sync, pool)
-    if rank == 0 and not a.no_roofline:
+        if a.full:
+            out['dp_timeline'] = dp_timeline(trainer, sync, pool)
+    if a.full and rank == 0 and not a.no_roofline:
         # dominant kernel family: the 3x3 convs (forward incl. the GroupNorm-prologue form, and data gradients)
         rec = LaunchRecorder()
         rec.install()
@@ -763,7 +805,7 @@ def main():
         dist.barrier()
 
     sampler_capture_failed = False
-    if not a.no_sampling:
+    if a.full and not a.no_sampling:
         # second headline metric (BASELINE configs[2]): DDIM-100 sampling, B = 256 per GPU.  The image batch is
         # sharded over the ranks with NO data-path collective; the barrier / MAX below only bracket the timing.
         from infodiffusion_amd.sampling import DiffusionProcess
@@ -814,7 +856,7 @@ def main():
         del proc, smodel
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not a.no_large_batch:
+    if a.full and rank == 0 and world == 1 and not a.no_large_batch:
         out['large_batch'] = large_batch_rate(a, margs, dev)
         if a.dtype == 'bf16':
             # the same step in the reference's own arithmetic (fp32 activations, exact-f32 MFMA): supplementary
@@ -836,11 +878,11 @@ def main():
             out['atomics_value'] = {'value': r['value'], 'unit': 'images/s', 'ms_per_step': r['ms_per_step'],
                                     'note': 'same step with fp32 atomics for the weight gradients and the GroupNorm parameter gradients '
                                             '(ops.set_deterministic(False)); `value` is the bit-reproducible default, B=%d, graph replay' % a.batch}
-    if rank == 0 and world == 1 and sync is None and not a.no_dp_probe:
+    if a.full and rank == 0 and world == 1 and sync is None and not a.no_dp_probe:
         out['dp_one_rank'] = one_rank_dp_cost(a)
         if 'ms_per_step' in out['dp_one_rank']:
             out['dp_one_rank']['delta_ms_vs_value'] = round(out['dp_one_rank']['ms_per_step'] - out['ms_per_step'], 3)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(margs)
     if dist.is_initialized():
         dist.barrier()

@@ -42,6 +42,29 @@ def test_cli_train_checkpoint_eval(tmp_path):
     assert img.shape == (16, 1, 32, 32) and np.isfinite(img).all()
 
 
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain bench.py run prints the headline line only (nothing of --full), times exactly --steps steps, and --dump-outputs
+    writes the last timed step's outputs as float32 .npy files of at most 64 MB together."""
+    import json
+    dump = str(tmp_path / 'dump')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', dump], cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'images/s' and d['higher_is_better'] is True and d['dtype'] == 'bf16'
+    assert d['ms_per_step'] > 0 and abs(d['value'] - 32 / (d['ms_per_step'] * 1e-3)) < 1e-2 * d['value']
+    for k in ('roofline', 'sampling', 'large_batch', 'fp32_value', 'atomics_value', 'dp_one_rank', 'cpu_baseline', 'parity'):
+        assert k not in d, k
+    got = {fn: np.load(os.path.join(dump, fn)) for fn in sorted(os.listdir(dump))}
+    assert sorted(got) == ['grad_norm.npy', 'grads.npy', 'loss.npy', 'params.npy']
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64e6
+    assert got['params.npy'].shape == got['grads.npy'].shape and got['grads.npy'].any()
+    assert abs(float(got['grad_norm.npy'][0]) - d['config']['last_grad_norm']) < 1e-3
+
+
 def test_cli_latent_pipeline(tmp_path):
     """Config-5 flow of the reference (run.py:415-443, 482-526, eval_fid.sh): train -> save_latent (the
     `{model}_{exp}_latent.npz` wire format) -> train_latent_ddim on it -> eval_fid --is_latent (latent DDIM

@@ -3,7 +3,7 @@
 for round in 1 2; do
 for v in "$@"; do
   if [ "$v" = default ]; then unset IDF_LIB; else export IDF_LIB=$PWD/infodiffusion_amd/variants/libinfodiff_hip_$v.so; fi
-  python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-large-batch 2>/dev/null | tail -1 > /tmp/_ab.json
+  python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-large-batch 2>/dev/null | tail -1 > /tmp/_ab.json
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open('/tmp/_ab.json'))

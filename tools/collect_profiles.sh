@@ -4,7 +4,7 @@
 tag=$1
 export TMPDIR=/tmp
 out=gpurun_out
-rocprofv3 --kernel-trace --stats -d $out/${tag}_p1 -o train -- python3 bench.py --no-cpu-baseline --no-large-batch --no-dp-probe > $out/${tag}_p1.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/${tag}_p1 -o train -- python3 bench.py --full --no-cpu-baseline --no-large-batch --no-dp-probe > $out/${tag}_p1.log 2>&1
 db=$(find $out/${tag}_p1 -name '*results.db' | head -1)
 python tools/step_inventory.py $db 80 > $out/${tag}_step_inventory.txt
 python tools/rocpd_stats.py $db $out/${tag}_kernel_stats.csv

@@ -676,8 +676,26 @@ def gen_latent_archive():
     print('wrote ref_diff_latent.npz %.1f KB' % (os.path.getsize(path + '.npz') / 1024))
 
 
+def gen_ckpt_init():
+    """The reference's own InfoDiff right after construction under torch.manual_seed(3) (the small configuration of
+    tests/test_cabi_exports.py::test_checkpoint_interchange_with_reference): every state_dict entry as (key, shape, dtype, SHA-256 of
+    its bytes in logical order) -- what a check-point of either side must hold for the other to load it strictly, and what a seeded
+    initialisation of the product must reproduce bit for bit."""
+    import hashlib
+    a = types.SimpleNamespace(beta1=1e-5, betaT=1e-2, diffusion_steps=100, input_size=32, is_bottleneck=False,
+                              unets_channels=32, encoder_channels=32, a_dim=16, mmd_weight=0.1, kld_weight=0.0)
+    torch.manual_seed(3)
+    ref = R_models.InfoDiff(a, 'cpu', (1, 32, 32))
+    rows = [[k, list(v.shape), str(v.dtype), hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest()]
+            for k, v in ref.state_dict().items()]
+    path = os.path.join(GOLD, 'ckpt_init_seed3.json')
+    with open(path, 'w') as f:
+        json.dump(rows, f, indent=0)
+    print('wrote ckpt_init_seed3.json: %d entries, %.1f KB' % (len(rows), os.path.getsize(path) / 1024))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['schedule', 'blocks', 'mmd', 'stub', 'latent', 'vanilla', 'fmnist', 'bneck', 'vae', 'priors', 'branches', 'size28', 'latent_archive', 'celeba', 'config5']
+    which = sys.argv[1:] or ['schedule', 'blocks', 'mmd', 'stub', 'latent', 'vanilla', 'fmnist', 'bneck', 'vae', 'priors', 'branches', 'size28', 'latent_archive', 'ckpt_init', 'celeba', 'config5']
     if 'schedule' in which:
         gen_schedule()
     if 'blocks' in which:
@@ -708,6 +726,8 @@ if __name__ == '__main__':
         gen_model('size28', O.Cfg(input_channels=1, unets_channels=32, encoder_channels=32, input_size=28, a_dim=32, mmd_weight=0.1), B=3, seed=69)
     if 'latent_archive' in which:
         gen_latent_archive()
+    if 'ckpt_init' in which:
+        gen_ckpt_init()
     if 'celeba' in which:
         gen_model('celeba', O.dataset_cfg('celeba', a_dim=32, mmd_weight=0.1), B=2, seed=64)
     if 'config5' in which:

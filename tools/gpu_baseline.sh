@@ -5,7 +5,7 @@ tag=$1
 export TMPDIR=/tmp
 out=gpurun_out
 mkdir -p $out
-python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-large-batch > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-large-batch > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 1500 $out/${tag}_bench.json
 rocprofv3 --kernel-trace --stats -d $out/${tag}_p1 -o train -- python3 bench.py --no-cpu-baseline --no-large-batch --no-roofline --no-sampling > $out/${tag}_p1.log 2>&1
 db=$(find $out/${tag}_p1 -name '*results.db' | head -1)
