@@ -55,6 +55,18 @@ int idf_conv2d_fwd(const void* x, const void* w, const float* bias, const void* 
                    int B, int Hs, int Ws, int Cin, int Ho, int Wo, int Cout, int mode, int taps, int act,
                    int dtype, void* stream);
 
+/* fp32 halo-tile form of the stride-1 3x3 conv (no prologue; zero padding) on the exact-fp32 MFMA:
+ *   y[b,oy,ox,n] = bias[n] + res[b,oy,ox,n] + sum_{ky,kx,c} x[b,oy+ky-1,ox+kx-1,c] * w[n][ky*3+kx][c]
+ * x [B,H,W,Cin], res / y [B,H,W,Cout] dense NHWC fp32, w [Cout][9][Cin] fp32 (the forward shadow of
+ * idf_pack_conv_weight; with the data-gradient shadow and dy as x it is the data gradient); bias and res may be
+ * NULL.  Every input element is read once per (pixel tile, cout tile) instead of once per tap; no atomics, fixed
+ * summation order.  idf_conv3x3_f32_ok (host only, no GPU call): 1 when the shape is covered -- Cin % 32 == 0,
+ * 4 <= W <= 64, H >= 4, any Cout; idf_conv3x3_f32 returns IDF_ERR_UNSUPPORTED before any launch otherwise: use
+ * idf_conv2d_fwd then. */
+int idf_conv3x3_f32(const float* x, const float* w, const float* bias, const float* res, float* y,
+                    int B, int H, int W, int Cin, int Cout, void* stream);
+int idf_conv3x3_f32_ok(int B, int H, int W, int Cin, int Cout);
+
 /* bf16 halo-tile form of the 3x3 conv (mode S1 / S2 / UP2 / T2, no prologue; H, W = output dims): one
  * input read per 32-channel chunk instead of one per tap.  IDF_ERR_UNSUPPORTED for shapes it does
  * not cover (Cin % 32, W not a power of two in 4..128): use idf_conv2d_fwd then.

@@ -144,6 +144,14 @@ def fewc_tiles(B, H, W, Cin, Cout):
     return int(_lib.load().idf_conv_fewc_tiles(B, H, W, Cin, Cout))
 
 
+_F32_HALO = True   # the fp32 stride-1 3x3 convs in the halo-tile form (idf_conv3x3_f32)
+
+
+@functools.lru_cache(maxsize=None)
+def f32_halo_ok(B, H, W, Cin, Cout):
+    return bool(_lib.load().idf_conv3x3_f32_ok(B, H, W, Cin, Cout))
+
+
 def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, act, Cout, out_hw_=None, want_stats=False):
     """x logical [B,Cin,Hs,Ws] NHWC-dense; w_fwd [Cout][taps][Cin] in x.dtype.  want_stats: returns (y, st) where
     st = the statistics partials of y (None when the kernel that ran does not produce them)."""
@@ -179,6 +187,10 @@ def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, a
             st = _new_stats(B, Ho, Wo, Cin, Cout, mode, 9, x.device)
         call('idf_conv3x3_bf16', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), B, Ho, Wo, Cin, Cout,
              {S1: 0, S2: 1, UP2: 2, T2: 3}[mode], _p(st), _st())
+        return done()
+    if x.dtype == torch.float32 and taps == 9 and mode == S1 and act == 0 and _F32_HALO and f32_halo_ok(B, Ho, Wo, Cin, Cout):
+        # fp32 3x3 (forward and stride-1 data gradient): halo slab staged once per 16-channel chunk, exact-fp32 MFMA
+        call('idf_conv3x3_f32', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), B, Ho, Wo, Cin, Cout, _st())
         return done()
     call('idf_conv2d_fwd', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), _p(sc), _p(sh), _p(seed),
          salt, float(p_drop), B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps, act, _dt(x), _st())
@@ -813,7 +825,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 
