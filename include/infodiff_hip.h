@@ -67,6 +67,22 @@ int idf_conv3x3_f32(const float* x, const float* w, const float* bias, const flo
                     int B, int H, int W, int Cin, int Cout, void* stream);
 int idf_conv3x3_f32_ok(int B, int H, int W, int Cin, int Cout);
 
+/* fp32 stride-1 weight gradient (taps 9: 3x3 with zero padding; taps 1) with the bias gradient fused in, on the
+ * exact-fp32 MFMA: no atomics, no zero-fill, fixed summation order (bit-identical run to run).
+ *   dW[n][tap][c] = sum_{b,oy,ox} dy[b,oy,ox,n] * a[b,oy+ky-1,ox+kx-1,c]   (tap = ky*3+kx; taps 1: a[b,oy,ox,c])
+ *   db[n]         = sum_{b,oy,ox} dy[b,oy,ox,n]
+ * a [B,H,W,Cin], dy [B,H,W,Cout] dense NHWC fp32, dW [Cout][taps][Cin] and db [Cout] fp32; every pointer 16-byte
+ * aligned.  db may be NULL.  Covered: Cin % 4 == 0, Cout % 4 == 0 (each <= 65536), 4 <= W <= 64, H >= 4, any B, every tensor under
+ * 2^31 elements.  idf_conv_wgrad_f32_plan (host only, no GPU call): 1 when covered, and writes the number of pixel
+ * splits S and the workspace size in floats: 0 when S == 1 (the workgroups store straight into dW / db), else
+ * S * (Cout * taps * Cin + Cout) -- one dW | db slab per split, rounded up to a multiple of 4 floats, which the
+ * channel conditions make it already; a reduce launch adds the slabs in slab order.  0: not covered, and
+ * idf_conv_wgrad_f32 returns IDF_ERR_UNSUPPORTED before any launch: use idf_conv2d_wgrad then.  ws may be NULL only
+ * when the plan says 0 floats (IDF_ERR_BADARG otherwise, as for NULL a, dy or dW). */
+int idf_conv_wgrad_f32_plan(int B, int H, int W, int Cin, int Cout, int taps, int* splits_out, long* ws_floats_out);
+int idf_conv_wgrad_f32(const float* a, const float* dy, float* dW, float* db, float* ws, int B, int H, int W,
+                       int Cin, int Cout, int taps, void* stream);
+
 /* bf16 halo-tile form of the 3x3 conv (mode S1 / S2 / UP2 / T2, no prologue; H, W = output dims): one
  * input read per 32-channel chunk instead of one per tap.  IDF_ERR_UNSUPPORTED for shapes it does
  * not cover (Cin % 32, W not a power of two in 4..128): use idf_conv2d_fwd then.
