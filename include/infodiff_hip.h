@@ -83,6 +83,28 @@ int idf_conv_wgrad_f32_plan(int B, int H, int W, int Cin, int Cout, int taps, in
 int idf_conv_wgrad_f32(const float* a, const float* dy, float* dW, float* db, float* ws, int B, int H, int W,
                        int Cin, int Cout, int taps, void* stream);
 
+/* Gather-mode variant of the same kernel for the fp32 weight gradients idf_conv_wgrad_f32 refuses; mode numbered as
+ * in idf_conv2d_wgrad (0 = S1, 1 = S2, 2 = UP2), a [B,Hs,Ws,Cin], dy [B,Ho,Wo,Cout] dense NHWC fp32, dW
+ * [Cout][taps][Cin], db [Cout] (may be NULL) fp32, db[n] = sum dy[...,n] from the same launch:
+ *   S1  (taps 9 or 1)  as above, any Cin >= 1 and Cout >= 1;   Ho = Hs, Wo = Ws, 4 <= Wo <= 64
+ *   S2  (taps 9)       dW[n][ky*3+kx][c] = sum dy[b,oy,ox,n] * a[b,2oy+ky-1,2ox+kx-1,c]
+ *                      Ho = (Hs+1)/2, Wo = (Ws+1)/2 (odd Hs / Ws: the right / bottom taps fall outside), 4 <= Wo <= 32
+ *   UP2 (taps 9)       dW[n][ky*3+kx][c] = sum dy[b,oy,ox,n] * a[b,(oy+ky-1)>>1,(ox+kx-1)>>1,c] over 0 <= oy+ky-1 < 2Hs,
+ *                      0 <= ox+kx-1 < 2Ws;   Ho = 2 Hs, Wo = 2 Ws, 4 <= Wo <= 64
+ * Ho >= 4, any B, any channel counts 1 .. 65536 in every mode (no padded copies: channel counts that are not
+ * multiples of 4 are staged with scalar loads; a and dy then need only 4-byte alignment), every tensor under 2^31
+ * elements.  Exact-fp32 MFMA, no atomics, no zero-fill, fixed summation order.  idf_conv_wgrad_f32_gather_plan (host
+ * only, no GPU call): 1 when covered, and writes the number of pixel splits S and the workspace size in floats -- 0
+ * when S == 1, else S slabs of round4(Cout * taps * Cin) + round4(Cout) floats; 0: not covered (this includes Ho / Wo
+ * that do not follow from Hs / Ws and the mode, and taps 1 with mode != S1), and idf_conv_wgrad_f32_gather returns
+ * IDF_ERR_UNSUPPORTED before any launch: use idf_conv2d_wgrad then.  S1 shapes that idf_conv_wgrad_f32 covers are
+ * handed to it unchanged.  ws may be NULL only when the plan says 0 floats (IDF_ERR_BADARG otherwise, as for NULL a,
+ * dy or dW). */
+int idf_conv_wgrad_f32_gather_plan(int B, int Hs, int Ws, int Cin, int Ho, int Wo, int Cout, int mode, int taps,
+                                   int* splits_out, long* ws_floats_out);
+int idf_conv_wgrad_f32_gather(const float* a, const float* dy, float* dW, float* db, float* ws, int B, int Hs, int Ws,
+                              int Cin, int Ho, int Wo, int Cout, int mode, int taps, void* stream);
+
 /* bf16 halo-tile form of the 3x3 conv (mode S1 / S2 / UP2 / T2, no prologue; H, W = output dims): one
  * input read per 32-channel chunk instead of one per tap.  IDF_ERR_UNSUPPORTED for shapes it does
  * not cover (Cin % 32, W not a power of two in 4..128): use idf_conv2d_fwd then.

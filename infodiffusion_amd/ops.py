@@ -167,6 +167,23 @@ def f32_wgrad_ok(B, H, W, Cin, Cout, taps):
     return _f32_wgrad_plan(B, H, W, Cin, Cout, taps) is not None
 
 
+# the fp32 weight gradients the stride-1 plan refuses (stride 2, up-sampling, channel counts that are not multiples of 4) in the
+# gather-mode variant of the ordered-slab kernel (idf_conv_wgrad_f32_gather)
+_F32_WGRAD_GATHER = True
+
+
+@functools.lru_cache(maxsize=None)
+def _f32_wgrad_gather_plan(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps):
+    """(pixel splits, workspace floats) of idf_conv_wgrad_f32_gather for this shape, None when it is not covered."""
+    s, n = ctypes.c_int(0), ctypes.c_long(0)
+    ok = _lib.load().idf_conv_wgrad_f32_gather_plan(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps, ctypes.byref(s), ctypes.byref(n))
+    return (s.value, n.value) if ok else None
+
+
+def f32_wgrad_gather_ok(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps):
+    return _f32_wgrad_gather_plan(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps) is not None
+
+
 def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, act, Cout, out_hw_=None, want_stats=False):
     """x logical [B,Cin,Hs,Ws] NHWC-dense; w_fwd [Cout][taps][Cin] in x.dtype.  want_stats: returns (y, st) where
     st = the statistics partials of y (None when the kernel that ran does not produce them)."""
@@ -840,7 +857,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_F32_HALO', '_F32_WGRAD', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 
@@ -1209,6 +1226,15 @@ def conv_wgrad_bias_raw(a, dy, mode, taps, want_bias, w_slot=None, b_slot=None, 
         nws = _f32_wgrad_plan(B, Ho, Wo, Cin, Cout, taps)[1]
         ws = torch.empty((nws,), dtype=torch.float32, device=a.device) if nws else None
         call('idf_conv_wgrad_f32', _p(a), _p(dy), _p(dW), _p(db), _p(ws), B, Ho, Wo, Cin, Cout, taps, _st())
+        return dW.permute(0, 3, 1, 2), db
+    if (a.dtype == torch.float32 and dy.dtype == torch.float32 and mode in (S1, S2, UP2) and _F32_WGRAD_GATHER
+            and f32_wgrad_gather_ok(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps)):
+        # the same kernel family over a strided / up-sampled / few-channel input tile
+        dW = torch.empty((Cout, k, k, Cin), dtype=torch.float32, device=a.device)
+        db = torch.empty((Cout,), dtype=torch.float32, device=a.device) if want_bias else None
+        nws = _f32_wgrad_gather_plan(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps)[1]
+        ws = torch.empty((nws,), dtype=torch.float32, device=a.device) if nws else None
+        call('idf_conv_wgrad_f32_gather', _p(a), _p(dy), _p(dW), _p(db), _p(ws), B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps, _st())
         return dW.permute(0, 3, 1, 2), db
     dW = conv_wgrad_raw(a, dy, None, None, None, 0, 0.0, mode, taps, 0)
     db = colsum_raw(dy.permute(0, 2, 3, 1).reshape(B * Ho * Wo, Cout)) if want_bias else None
