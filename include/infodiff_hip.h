@@ -67,6 +67,30 @@ int idf_conv3x3_f32(const float* x, const float* w, const float* bias, const flo
                     int B, int H, int W, int Cin, int Cout, void* stream);
 int idf_conv3x3_f32_ok(int B, int H, int W, int Cin, int Cout);
 
+/* fp32 DownSample (3x3, stride 2, pad 1: modules.py:66) and UpSample (nearest x2 + 3x3: modules.py:89-92) convs, forward
+ * and data gradient, on the exact-fp32 MFMA in the halo-slab form of idf_conv3x3_f32, without the products that are known:
+ * Hs, Ws, Cin, Cout are always the FORWARD conv's input map and channels; op selects
+ *   IDF_RESAMPLE_S2_FWD     x [B,Hs,Ws,Cin] -> y [B,(Hs+1)/2,(Ws+1)/2,Cout], w = forward shadow [Cout][9][Cin]
+ *   IDF_RESAMPLE_S2_DGRAD   x = dy [B,Hs/2,Ws/2,Cout] -> y = dx [B,Hs,Ws,Cin], w = data-gradient shadow [Cin][9 flipped][Cout];
+ *                           Hs, Ws even; per output parity only the taps that land on a dy pixel (9 per four outputs, not 36)
+ *   IDF_RESAMPLE_UP2_FWD    x [B,Hs,Ws,Cin] -> y [B,2Hs,2Ws,Cout], forward shadow; 4 summed taps per output pixel, not 9
+ *   IDF_RESAMPLE_UP2_DGRAD  x = dy [B,2Hs,2Ws,Cout] -> y = dx [B,Hs,Ws,Cin], data-gradient shadow; one 4x4 stride-2 conv with
+ *                           summed taps (16 per dx pixel) = the flipped 3x3 over dy followed by the 2x2 sum pool
+ * all dense NHWC fp32; bias [rows of w] and res (shaped as y) may be NULL and are added in the epilogue.  Summed weights are
+ * added in registers from the 3x3 shadow, kernel rows first, then columns.  No atomics, fixed summation order.  Covered: K-side
+ * channels (Cin forward, Cout data gradient) % 32 == 0, any row-side count, tile-map width (S2: output, UP2: input) 4 .. 32 and
+ * height >= 2; not the S2 forward whose launch would fill the chip (>= 512 workgroups of 32 output pixels x 64 couts) nor the
+ * UP2 data gradient of maps of <= 64 pixels at B >= 32, where the older route measured faster.
+ * idf_conv_resample_f32_ok (host only, no GPU call): 1 when covered; otherwise idf_conv_resample_f32 returns
+ * IDF_ERR_UNSUPPORTED before any launch: use idf_conv2d_fwd (and idf_pool2_sum) then. */
+#define IDF_RESAMPLE_S2_FWD 0
+#define IDF_RESAMPLE_S2_DGRAD 1
+#define IDF_RESAMPLE_UP2_FWD 2
+#define IDF_RESAMPLE_UP2_DGRAD 3
+int idf_conv_resample_f32(const float* x, const float* w, const float* bias, const float* res, float* y,
+                          int B, int Hs, int Ws, int Cin, int Cout, int op, void* stream);
+int idf_conv_resample_f32_ok(int B, int Hs, int Ws, int Cin, int Cout, int op);
+
 /* fp32 stride-1 weight gradient (taps 9: 3x3 with zero padding; taps 1) with the bias gradient fused in, on the
  * exact-fp32 MFMA: no atomics, no zero-fill, fixed summation order (bit-identical run to run).
  *   dW[n][tap][c] = sum_{b,oy,ox} dy[b,oy,ox,n] * a[b,oy+ky-1,ox+kx-1,c]   (tap = ky*3+kx; taps 1: a[b,oy,ox,c])

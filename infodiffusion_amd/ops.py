@@ -184,6 +184,17 @@ def f32_wgrad_gather_ok(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps):
     return _f32_wgrad_gather_plan(B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps) is not None
 
 
+# the fp32 DownSample / UpSample 3x3 convs, forward and data gradient, in the strided / sub-pixel halo-slab forms
+# (idf_conv_resample_f32); Hs, Ws, Cin, Cout: the forward conv's input map and channels
+_F32_RESAMPLE = True
+RS_S2_FWD, RS_S2_DGRAD, RS_UP2_FWD, RS_UP2_DGRAD = 0, 1, 2, 3
+
+
+@functools.lru_cache(maxsize=None)
+def f32_resample_ok(B, Hs, Ws, Cin, Cout, op):
+    return bool(_lib.load().idf_conv_resample_f32_ok(B, Hs, Ws, Cin, Cout, op))
+
+
 def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, act, Cout, out_hw_=None, want_stats=False):
     """x logical [B,Cin,Hs,Ws] NHWC-dense; w_fwd [Cout][taps][Cin] in x.dtype.  want_stats: returns (y, st) where
     st = the statistics partials of y (None when the kernel that ran does not produce them)."""
@@ -223,6 +234,13 @@ def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, a
     if x.dtype == torch.float32 and taps == 9 and mode == S1 and act == 0 and _F32_HALO and f32_halo_ok(B, Ho, Wo, Cin, Cout):
         # fp32 3x3 (forward and stride-1 data gradient): halo slab staged once per 16-channel chunk, exact-fp32 MFMA
         call('idf_conv3x3_f32', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), B, Ho, Wo, Cin, Cout, _st())
+        return done()
+    if (x.dtype == torch.float32 and taps == 9 and mode in (S2, UP2) and act == 0 and _F32_RESAMPLE
+            and (Ho, Wo) == out_hw(mode, Hs, Ws)
+            and f32_resample_ok(B, Hs, Ws, Cin, Cout, RS_S2_FWD if mode == S2 else RS_UP2_FWD)):
+        # fp32 DownSample / UpSample forward: de-interleaved stride-2 slab / four sub-pixel classes with summed taps
+        call('idf_conv_resample_f32', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), B, Hs, Ws, Cin, Cout,
+             RS_S2_FWD if mode == S2 else RS_UP2_FWD, _st())
         return done()
     call('idf_conv2d_fwd', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), _p(sc), _p(sh), _p(seed),
          salt, float(p_drop), B, Hs, Ws, Cin, Ho, Wo, Cout, mode, taps, act, _dt(x), _st())
@@ -396,8 +414,22 @@ def conv_dgrad_raw(dy, w_dgrad, mode_fwd, taps, x_shape, residual=None, shadows=
                 call('idf_downconv_dgrad_bf16', _p(_nhwc(dy)), _p(frag), _p(_nhwc(residual) if residual is not None else None),
                      _p(out), B, Hs // 2, Ws // 2, Cin, dy.shape[1], _st())
                 return out
+        if (dy.dtype == torch.float32 and dy.is_cuda and taps == 9 and _F32_RESAMPLE
+                and tuple(dy.shape[2:]) == out_hw(S2, Hs, Ws) and f32_resample_ok(B, Hs, Ws, Cin, dy.shape[1], RS_S2_DGRAD)):
+            # fp32 DownSample: the 9 taps spread over the four output parities, residual in the epilogue
+            out = empty_nhwc(B, Cin, Hs, Ws, dy.dtype, dy.device)
+            call('idf_conv_resample_f32', _p(_nhwc(dy)), _p(w_dgrad), None, _p(_nhwc(residual) if residual is not None else None),
+                 _p(out), B, Hs, Ws, Cin, dy.shape[1], RS_S2_DGRAD, _st())
+            return out
         return conv_raw(dy, w_dgrad, None, residual, None, None, None, 0, 0.0, T2, taps, 0, Cin, (Hs, Ws))
     if mode_fwd == UP2:
+        if (dy.dtype == torch.float32 and dy.is_cuda and taps == 9 and _F32_RESAMPLE
+                and tuple(dy.shape[2:]) == (2 * Hs, 2 * Ws) and f32_resample_ok(B, Hs, Ws, Cin, dy.shape[1], RS_UP2_DGRAD)):
+            # fp32 UpSample: flipped 3x3 + 2x2 sum pool as one 4x4 stride-2 conv with summed taps, residual in the epilogue
+            out = empty_nhwc(B, Cin, Hs, Ws, dy.dtype, dy.device)
+            call('idf_conv_resample_f32', _p(_nhwc(dy)), _p(w_dgrad), None, _p(_nhwc(residual) if residual is not None else None),
+                 _p(out), B, Hs, Ws, Cin, dy.shape[1], RS_UP2_DGRAD, _st())
+            return out
         up = conv_raw(dy, w_dgrad, None, None, None, None, None, 0, 0.0, S1, taps, 0, Cin)
         out = empty_nhwc(B, Cin, Hs, Ws, dy.dtype, dy.device)
         call('idf_pool2_sum', _p(up), _p(out), B, Hs, Ws, Cin, _dt(dy), _st())
