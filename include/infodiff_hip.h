@@ -593,6 +593,18 @@ int idf_attn_bwd(const void* qkv, const void* dO, const float* lse, float* dsum,
 int idf_attn_bwd_o(const void* qkv, const void* dO, const float* lse, const void* o, void* dqkv, int B, int N, int D,
                    float scale, int dtype, void* stream);
 
+/* The same attention in fp32 on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32), one launch forward and one backward: K and V
+ * (forward, query half of the backward) or Q and dO (key/value half) stream through LDS in row chunks, scores and probabilities
+ * stay in registers; fixed summation order, no atomics, bit-identical run to run.  Operands as idf_attn_fwd / idf_attn_bwd_o, all
+ * fp32, every pointer 16-byte aligned; lse [B, N] is private to this pair (base 2, of the scaled scores) and is NOT the lse of
+ * idf_attn_fwd.  Covered: N in {64, 256}, D in {64, 128}, 0 <= B <= 65535, except N = 256 with D = 128 at 0 < B < 128, where the
+ * older route measured faster.  idf_attn_f32_ok (host only, no GPU call): 1 when
+ * covered; otherwise both entries return IDF_ERR_UNSUPPORTED before any launch: use idf_bgemm + idf_softmax_* then. */
+int idf_attn_f32_ok(int B, int N, int D);
+int idf_attn_f32_fwd(const float* qkv, float* o, float* lse, int B, int N, int D, float scale, void* stream);
+int idf_attn_f32_bwd(const float* qkv, const float* dO, const float* lse, const float* o, float* dqkv, int B, int N, int D,
+                     float scale, void* stream);
+
 /* The proj conv folded into V (round 4): (P V) Wp^T = P (V Wp^T), so with Wv' = Wp Wv and b' = Wp bv + bp (the rows of P sum to one:
  * a bias on V' passes through the product unchanged) the block is y = x + P V' -- no proj launch, no proj data gradient, no proj weight
  * gradient.  idf_attn_fold_batched: Wv' [C][C] and (bq | bk | b') [3C] of every attention block of a network in one launch -- table

@@ -195,6 +195,15 @@ def f32_resample_ok(B, Hs, Ws, Cin, Cout, op):
     return bool(_lib.load().idf_conv_resample_f32_ok(B, Hs, Ws, Cin, Cout, op))
 
 
+# the fp32 attention (N tokens, C channels) as one streaming MFMA launch forward and one backward (idf_attn_f32_fwd / _bwd)
+_F32_ATTN = True
+
+
+@functools.lru_cache(maxsize=None)
+def f32_attn_ok(B, N, C):
+    return bool(_lib.load().idf_attn_f32_ok(B, N, C))
+
+
 def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, act, Cout, out_hw_=None, want_stats=False):
     """x logical [B,Cin,Hs,Ws] NHWC-dense; w_fwd [Cout][taps][Cin] in x.dtype.  want_stats: returns (y, st) where
     st = the statistics partials of y (None when the kernel that ran does not produce them)."""
@@ -889,7 +898,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_F32_HALO', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 
@@ -1993,7 +2002,14 @@ class _Attention(torch.autograd.Function):
         C, N = C3 // 3, H * W
         dev, dt = qkv.device, qkv.dtype
         ctx.fused = bool(_lib.load().idf_attn_fused_ok(N, C, _dt(qkv)))
-        if pre is not None:         # (o, lse) of the one-launch attention block: record the backward pass only
+        ctx.f32 = dt == torch.float32 and qkv.is_cuda and pre is None and _F32_ATTN and f32_attn_ok(B, N, C)
+        if ctx.f32:         # one launch, K and V streamed through LDS, scores and probabilities in registers
+            o = empty_nhwc(B, C, H, W, dt, dev)
+            lse = torch.empty((B, N), dtype=torch.float32, device=dev)
+            call('idf_attn_f32_fwd', _p(qkv), _p(o), _p(lse), B, N, C, float(int(C) ** (-0.5)), _st())
+            ctx.save_for_backward(qkv, lse, o)
+            return o
+        if pre is not None:        # (o, lse) of the one-launch attention block: record the backward pass only
             o, lse = pre
             ctx.save_for_backward(qkv, lse, o)
             return o
@@ -2020,6 +2036,9 @@ class _Attention(torch.autograd.Function):
         do = _nhwc(do.to(qkv.dtype))
         scale = float(int(C) ** (-0.5))
         dqkv = torch.empty_like(qkv, memory_format=CL)
+        if ctx.f32:                          # P is the row logsumexp of idf_attn_f32_fwd
+            call('idf_attn_f32_bwd', _p(qkv), _p(do), _p(P), _p(ctx.saved_tensors[2]), _p(dqkv), B, N, C, scale, _st())
+            return dqkv, None
         if ctx.fused:                        # P is the saved row logsumexp here
             if _ATTN_BWD_ONE:
                 call('idf_attn_bwd_o', _p(qkv), _p(do), _p(P), _p(ctx.saved_tensors[2]), _p(dqkv), B, N, C, scale, _dt(qkv), _st())
