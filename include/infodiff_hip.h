@@ -67,6 +67,23 @@ int idf_conv3x3_f32(const float* x, const float* w, const float* bias, const flo
                     int B, int H, int W, int Cin, int Cout, void* stream);
 int idf_conv3x3_f32_ok(int B, int H, int W, int Cin, int Cout);
 
+/* The same conv in the split-bf16 arithmetic modes of the fp32 path (gfx950 has no xf32 MFMA): each fp32 operand is written as
+ * terms = 3 (bf16x3) or 2 (bf16x2) bf16 terms, round-to-nearest-even, and only the significant cross products are formed on the
+ * bf16 MFMA into one fp32 accumulator (6 resp. 3 products per K step, smallest first) -- bf16x3 is fp32-grade (< 3 * 2^-27 per
+ * product dropped), bf16x2 keeps 3 * 2^-18 per product.  Same contract as idf_conv3x3_f32 (with the data-gradient shadow and dy
+ * it is the data gradient; bias / res may be NULL; no atomics, fixed summation order), except that the weights arrive pre-split:
+ * idf_split_weight_bf16 turns an fp32 shadow w [rows][taps][Cin] into the fragment-major bf16 shadow wsplit of
+ * idf_split_weight_bytes(rows, taps, Cin, terms) = (rows rounded up to 16) * taps * Cin * 2 * terms bytes (16-byte aligned, caller-
+ * owned; Cin % 32 == 0).  idf_conv3x3_f32_split_ok (host only, no GPU call): 1 when covered -- Cin % 32 == 0, 4 <= W <= 64,
+ * H >= 4, any Cout, terms 2 or 3 (not terms 2 on maps of <= 64 pixels at B >= 32, where the exact kernel measured no slower);
+ * idf_conv3x3_f32_split returns IDF_ERR_UNSUPPORTED before any launch otherwise.  Non-finite
+ * inputs, and magnitudes that round to the bf16 infinity, give non-finite outputs. */
+int idf_conv3x3_f32_split(const float* x, const void* wsplit, const float* bias, const float* res, float* y,
+                          int B, int H, int W, int Cin, int Cout, int terms, void* stream);
+int idf_conv3x3_f32_split_ok(int B, int H, int W, int Cin, int Cout, int terms);
+int idf_split_weight_bf16(const float* w, void* wsplit, int rows, int taps, int Cin, int terms, void* stream);
+long idf_split_weight_bytes(int rows, int taps, int Cin, int terms);
+
 /* fp32 DownSample (3x3, stride 2, pad 1: modules.py:66) and UpSample (nearest x2 + 3x3: modules.py:89-92) convs, forward
  * and data gradient, on the exact-fp32 MFMA in the halo-slab form of idf_conv3x3_f32, without the products that are known:
  * Hs, Ws, Cin, Cout are always the FORWARD conv's input map and channels; op selects

@@ -51,6 +51,10 @@ SIGNATURES = {
     'idf_conv2d_fwd': ([_p, _p, _p, _p, _p, _p, _p, _p, _u32, _f] + [_i] * 11 + [_p], C.c_int),
     'idf_conv3x3_f32': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], C.c_int),
     'idf_conv3x3_f32_ok': ([_i] * 5, C.c_int),
+    'idf_conv3x3_f32_split': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], C.c_int),
+    'idf_conv3x3_f32_split_ok': ([_i] * 6, C.c_int),
+    'idf_split_weight_bf16': ([_p, _p, _i, _i, _i, _i, _p], C.c_int),
+    'idf_split_weight_bytes': ([_i] * 4, C.c_long),
     'idf_conv_resample_f32': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], C.c_int),
     'idf_conv_resample_f32_ok': ([_i] * 6, C.c_int),
     'idf_conv_wgrad_f32_plan': ([_i] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_long)], C.c_int),

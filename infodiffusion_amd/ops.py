@@ -152,6 +152,35 @@ def f32_halo_ok(B, H, W, Cin, Cout):
     return bool(_lib.load().idf_conv3x3_f32_ok(B, H, W, Cin, Cout))
 
 
+# the fp32 stride-1 3x3 convs (forward and data gradient) on split-bf16 MFMA operands (idf_conv3x3_f32_split): 0 exact (default),
+# 3 = bf16x3 (fp32-grade), 2 = bf16x2 (3 * 2^-18 per product).  Weight gradients, resample convs, 1x1 convs and attention stay exact.
+_F32_SPLIT = 0
+_F32_MFMA_MODES = {'exact': 0, 'bf16x3': 3, 'bf16x2': 2}
+
+
+def set_f32_mfma(mode):
+    """Arithmetic of the fp32 stride-1 3x3 convs: 'exact' (fp32 MFMA, the default), 'bf16x3' or 'bf16x2' (split-bf16 MFMA).
+    Set it before a model is captured: a captured graph keeps the launches it recorded."""
+    global _F32_SPLIT
+    if mode not in _F32_MFMA_MODES:
+        raise ValueError("f32 mfma mode must be 'exact', 'bf16x3' or 'bf16x2', not %r" % (mode,))
+    _F32_SPLIT = _F32_MFMA_MODES[mode]
+
+
+def get_f32_mfma():
+    return {v: k for k, v in _F32_MFMA_MODES.items()}[_F32_SPLIT]
+
+
+@functools.lru_cache(maxsize=None)
+def f32_split_ok(B, H, W, Cin, Cout, terms):
+    return bool(_lib.load().idf_conv3x3_f32_split_ok(B, H, W, Cin, Cout, terms))
+
+
+@functools.lru_cache(maxsize=None)
+def _split_weight_bytes(rows, taps, Cin, terms):
+    return int(_lib.load().idf_split_weight_bytes(rows, taps, Cin, terms))
+
+
 _F32_WGRAD = True  # the fp32 stride-1 weight gradients (3x3, 1x1) + bias gradient in the ordered-slab MFMA form (idf_conv_wgrad_f32)
 
 
@@ -239,6 +268,14 @@ def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, a
             st = _new_stats(B, Ho, Wo, Cin, Cout, mode, 9, x.device)
         call('idf_conv3x3_bf16', _p(x), _p(w_fwd), _p(bias), _p(residual), _p(y), B, Ho, Wo, Cin, Cout,
              {S1: 0, S2: 1, UP2: 2, T2: 3}[mode], _p(st), _st())
+        return done()
+    if (x.dtype == torch.float32 and taps == 9 and mode == S1 and act == 0 and _F32_SPLIT
+            and f32_split_ok(B, Ho, Wo, Cin, Cout, _F32_SPLIT)):
+        # fp32 3x3 on split-bf16 MFMA operands.  The split shadow is made per call, on the same stream: it is captured with the
+        # step, so a graph replay always sees the current weights
+        ws = torch.empty((_split_weight_bytes(Cout, 9, Cin, _F32_SPLIT),), dtype=torch.uint8, device=x.device)
+        call('idf_split_weight_bf16', _p(w_fwd), _p(ws), Cout, 9, Cin, _F32_SPLIT, _st())
+        call('idf_conv3x3_f32_split', _p(x), _p(ws), _p(bias), _p(residual), _p(y), B, Ho, Wo, Cin, Cout, _F32_SPLIT, _st())
         return done()
     if x.dtype == torch.float32 and taps == 9 and mode == S1 and act == 0 and _F32_HALO and f32_halo_ok(B, Ho, Wo, Cin, Cout):
         # fp32 3x3 (forward and stride-1 data gradient): halo slab staged once per 16-channel chunk, exact-fp32 MFMA
@@ -898,7 +935,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_F32_HALO', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_F32_SPLIT', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 

@@ -7,7 +7,8 @@
 
 Modes: train, eval, eval_fid, save_latent, train_latent_ddim, and the latent-editing callers of the samplers
 (interpolate / disentangle / latent_quality), plot_latent (matplotlib scatter) and save_original_img.
-Extra flags: --act_dtype {bf16 (default), fp32}, --steps_per_epoch N (synthetic data), --graph {0,1}.
+Extra flags: --act_dtype {bf16 (default), fp32}, --f32_mfma {exact (default), bf16x3, bf16x2} (with --act_dtype fp32),
+--steps_per_epoch N (synthetic data), --graph {0,1}.
 Images are written as .npy (torchvision is not available in this image).
 """
 import argparse
@@ -70,9 +71,15 @@ def parse_args(argv=None):
                    help='activation / weight-shadow storage of the kernels: bf16 (MFMA bf16, ~9x faster; loss within 1e-2 of '
                         'the reference, epsilon-hat within 2e-2: DESIGN.md section 2) or fp32 (exact-f32 MFMA; within '
                         '1e-4 of the reference)')
+    p.add_argument('--f32_mfma', default='exact', choices=['exact', 'bf16x3', 'bf16x2'],
+                   help='arithmetic of the fp32 stride-1 3x3 convs (forward and data gradient) with --act_dtype fp32: exact fp32 MFMA, '
+                        'or split-bf16 MFMA operands -- bf16x3 (fp32-grade) / bf16x2 (3 * 2^-18 per product); everything else stays exact')
     p.add_argument('--steps_per_epoch', type=int, default=100)
     p.add_argument('--graph', type=int, default=1, help='replay the train step from a captured hipGraph')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.f32_mfma != 'exact' and args.act_dtype != 'fp32':
+        p.error('--f32_mfma %s needs --act_dtype fp32' % args.f32_mfma)
+    return args
 
 
 def _dist_setup():
@@ -309,6 +316,9 @@ def evaluate(args):
 
 if __name__ == '__main__':
     args = parse_args()
+    if args.f32_mfma != 'exact':
+        from infodiffusion_amd import ops
+        ops.set_f32_mfma(args.f32_mfma)       # before any model is built or captured
     if args.mode == 'save_original_img':
         # reference run.py:540-549: the dataset's images in [0, 1] (here as .npy batches; no model, no GPU kernels)
         out = './%s_imgs/' % args.dataset
