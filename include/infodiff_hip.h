@@ -124,6 +124,19 @@ int idf_conv_wgrad_f32_plan(int B, int H, int W, int Cin, int Cout, int taps, in
 int idf_conv_wgrad_f32(const float* a, const float* dy, float* dW, float* db, float* ws, int B, int H, int W,
                        int Cin, int Cout, int taps, void* stream);
 
+/* The same weight gradient in the split-bf16 arithmetic modes of the fp32 path: a and dy are both split on the fly into terms = 3
+ * (bf16x3) or 2 (bf16x2) bf16 terms, round-to-nearest-even, and the kept cross products (6 resp. 3 per 32-pixel K step, smallest
+ * first) go to the bf16 MFMA into one fp32 accumulator; db stays an exact fp32 sum.  Same tensors, same contract and the same
+ * workspace layout, S * (Cout * taps * Cin + Cout) floats, as idf_conv_wgrad_f32: caller-owned workspace, db may be NULL, ws may be
+ * NULL only when the plan says 0 floats, no atomics, no zero-fill, fixed summation order (bit-identical run to run).  Covered:
+ * terms 2 or 3, taps 9 or 1, Cin % 8 == 0, Cout % 8 == 0 (each <= 65536), 4 <= W <= 64, H >= 4, any B, every tensor under 2^31
+ * elements.  idf_conv_wgrad_f32_split_plan (host only, no GPU call): 1 when covered; 0: not covered, and idf_conv_wgrad_f32_split
+ * returns IDF_ERR_UNSUPPORTED before any launch: use idf_conv_wgrad_f32 then.  Non-finite inputs, and magnitudes that round to the
+ * bf16 infinity, give non-finite outputs. */
+int idf_conv_wgrad_f32_split_plan(int B, int H, int W, int Cin, int Cout, int taps, int terms, int* splits_out, long* ws_floats_out);
+int idf_conv_wgrad_f32_split(const float* a, const float* dy, float* dW, float* db, float* ws, int B, int H, int W,
+                             int Cin, int Cout, int taps, int terms, void* stream);
+
 /* Gather-mode variant of the same kernel for the fp32 weight gradients idf_conv_wgrad_f32 refuses; mode numbered as
  * in idf_conv2d_wgrad (0 = S1, 1 = S2, 2 = UP2), a [B,Hs,Ws,Cin], dy [B,Ho,Wo,Cout] dense NHWC fp32, dW
  * [Cout][taps][Cin], db [Cout] (may be NULL) fp32, db[n] = sum dy[...,n] from the same launch:

@@ -59,6 +59,8 @@ SIGNATURES = {
     'idf_conv_resample_f32_ok': ([_i] * 6, C.c_int),
     'idf_conv_wgrad_f32_plan': ([_i] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_long)], C.c_int),
     'idf_conv_wgrad_f32': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], C.c_int),
+    'idf_conv_wgrad_f32_split_plan': ([_i] * 7 + [C.POINTER(C.c_int), C.POINTER(C.c_long)], C.c_int),
+    'idf_conv_wgrad_f32_split': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], C.c_int),
     'idf_conv_wgrad_f32_gather_plan': ([_i] * 9 + [C.POINTER(C.c_int), C.POINTER(C.c_long)], C.c_int),
     'idf_conv_wgrad_f32_gather': ([_p] * 5 + [_i] * 9 + [_p], C.c_int),
     'idf_conv3x3_bf16': ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p], C.c_int),

@@ -15,6 +15,7 @@ EXTRA = {'idf_elementwise.hip': ['-ffp-contract=off'],
          'idf_conv3x3_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_conv3x3_split.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_wgrad_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+         'idf_wgrad_split.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_conv_resample_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_attn_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 

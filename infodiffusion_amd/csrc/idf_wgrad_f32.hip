@@ -49,6 +49,7 @@
 // The gather-mode variant (wgrad_f32_gather_kernel, idf_conv_wgrad_f32_gather: stride 2, x2 up-sampling, channel counts
 // that are not multiples of 4) shares all of the above; its staging layouts and bank arithmetic are described above it.
 #include "idf_common.h"
+#include "idf_wgrad_f32_parts.h"
 
 namespace {
 
@@ -242,20 +243,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(const WgP p) {
       ob[n0 + tid] = v;
     }
   }
-}
-
-// dW | db = sum of the S slabs, in slab order; one float4 per thread (nW % 4 == 0: no float4 straddles dW | db)
-__global__ __launch_bounds__(256) void wgrad_f32_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dW,
-                                                               float* __restrict__ db, long nW, long n4, long slab, int S) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const long e = 4 * i;
-  float4 v = *reinterpret_cast<const float4*>(ws + e);
-  for (int s = 1; s < S; ++s) {
-    const float4 u = *reinterpret_cast<const float4*>(ws + (size_t)s * slab + e);
-    v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-  }
-  *reinterpret_cast<float4*>(e < nW ? dW + e : db + (e - nW)) = v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

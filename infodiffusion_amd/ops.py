@@ -152,14 +152,17 @@ def f32_halo_ok(B, H, W, Cin, Cout):
     return bool(_lib.load().idf_conv3x3_f32_ok(B, H, W, Cin, Cout))
 
 
-# the fp32 stride-1 3x3 convs (forward and data gradient) on split-bf16 MFMA operands (idf_conv3x3_f32_split): 0 exact (default),
-# 3 = bf16x3 (fp32-grade), 2 = bf16x2 (3 * 2^-18 per product).  Weight gradients, resample convs, 1x1 convs and attention stay exact.
+# the fp32 stride-1 3x3 convs (forward and data gradient, idf_conv3x3_f32_split) and the stride-1 weight gradients (3x3 and 1x1,
+# idf_conv_wgrad_f32_split) on split-bf16 MFMA operands: 0 exact (default), 3 = bf16x3 (fp32-grade), 2 = bf16x2 (3 * 2^-18 per product).
+# Bias gradients, the gather-mode (stride-2, up-sampling, few-channel) weight gradients, resample convs, 1x1 forward convs and
+# attention stay exact.
 _F32_SPLIT = 0
 _F32_MFMA_MODES = {'exact': 0, 'bf16x3': 3, 'bf16x2': 2}
 
 
 def set_f32_mfma(mode):
-    """Arithmetic of the fp32 stride-1 3x3 convs: 'exact' (fp32 MFMA, the default), 'bf16x3' or 'bf16x2' (split-bf16 MFMA).
+    """Arithmetic of the fp32 stride-1 3x3 convs (forward, data gradient) and of the stride-1 3x3 / 1x1 weight gradients: 'exact'
+    (fp32 MFMA, the default), 'bf16x3' or 'bf16x2' (split-bf16 MFMA).  Everything else in the fp32 path stays exact in every mode.
     Set it before a model is captured: a captured graph keeps the launches it recorded."""
     global _F32_SPLIT
     if mode not in _F32_MFMA_MODES:
@@ -194,6 +197,23 @@ def _f32_wgrad_plan(B, H, W, Cin, Cout, taps):
 
 def f32_wgrad_ok(B, H, W, Cin, Cout, taps):
     return _f32_wgrad_plan(B, H, W, Cin, Cout, taps) is not None
+
+
+# in the split modes (_F32_SPLIT != 0) the stride-1 weight gradients run on split-bf16 operands too (idf_conv_wgrad_f32_split);
+# False: they stay on the exact route above
+_F32_SPLIT_WGRAD = True
+
+
+@functools.lru_cache(maxsize=None)
+def _f32_wgrad_split_plan(B, H, W, Cin, Cout, taps, terms):
+    """(pixel splits, workspace floats) of idf_conv_wgrad_f32_split for this shape, None when it is not covered."""
+    s, n = ctypes.c_int(0), ctypes.c_long(0)
+    ok = _lib.load().idf_conv_wgrad_f32_split_plan(B, H, W, Cin, Cout, taps, terms, ctypes.byref(s), ctypes.byref(n))
+    return (s.value, n.value) if ok else None
+
+
+def f32_wgrad_split_ok(B, H, W, Cin, Cout, taps, terms):
+    return _f32_wgrad_split_plan(B, H, W, Cin, Cout, taps, terms) is not None
 
 
 # the fp32 weight gradients the stride-1 plan refuses (stride 2, up-sampling, channel counts that are not multiples of 4) in the
@@ -935,7 +955,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_F32_HALO', '_F32_SPLIT', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_F32_SPLIT', '_F32_SPLIT_WGRAD', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 
@@ -1296,6 +1316,15 @@ def conv_wgrad_bias_raw(a, dy, mode, taps, want_bias, w_slot=None, b_slot=None, 
             db = buf[nW:] if want_bias else None
             call('idf_conv_wgrad_bf16', _p(ap), _p(dyp), _p(dW), _p(db), B, Ho, Wo, Cip, Cop, Cin, Cout, taps, mode, 0, _st())
             return dW.permute(0, 3, 1, 2), db
+    if (a.dtype == torch.float32 and dy.dtype == torch.float32 and mode == S1 and _F32_SPLIT and _F32_SPLIT_WGRAD
+            and f32_wgrad_split_ok(B, Ho, Wo, Cin, Cout, taps, _F32_SPLIT)):
+        # the same ordered slabs on split-bf16 operands (both split on the fly); db stays an exact fp32 sum
+        dW = torch.empty((Cout, k, k, Cin), dtype=torch.float32, device=a.device)
+        db = torch.empty((Cout,), dtype=torch.float32, device=a.device) if want_bias else None
+        nws = _f32_wgrad_split_plan(B, Ho, Wo, Cin, Cout, taps, _F32_SPLIT)[1]
+        ws = torch.empty((nws,), dtype=torch.float32, device=a.device) if nws else None
+        call('idf_conv_wgrad_f32_split', _p(a), _p(dy), _p(dW), _p(db), _p(ws), B, Ho, Wo, Cin, Cout, taps, _F32_SPLIT, _st())
+        return dW.permute(0, 3, 1, 2), db
     if (a.dtype == torch.float32 and dy.dtype == torch.float32 and mode == S1 and _F32_WGRAD
             and f32_wgrad_ok(B, Ho, Wo, Cin, Cout, taps)):
         # ordered slabs on the exact-fp32 MFMA: no zero-fill, no atomics, db from the same launch
