@@ -635,6 +635,17 @@ int idf_attn_f32_fwd(const float* qkv, float* o, float* lse, int B, int N, int D
 int idf_attn_f32_bwd(const float* qkv, const float* dO, const float* lse, const float* o, float* dqkv, int B, int N, int D,
                      float scale, void* stream);
 
+/* The same fp32 attention with the matrix products on split-bf16 operands (v_mfma_f32_16x16x32_bf16; terms = 3: bf16x3, fp32-grade,
+ * terms = 2: bf16x2, 3 * 2^-18 per product), the attention of the fp32 modes of idf_conv3x3_f32_split.  Operands, alignment and
+ * the meaning of lse as idf_attn_f32_fwd / _bwd; softmax (max, exp2, sum) stays fp32; the backward consumes the lse and o of a
+ * forward with the same terms.  Fixed summation order, no atomics, bit-identical run to run.  Covered: terms in {2, 3}, N in
+ * {64, 256}, D in {64, 128}, 0 <= B <= 65535.  idf_attn_f32_split_ok (host only, no GPU call): 1 when covered; otherwise both
+ * entries return IDF_ERR_UNSUPPORTED before any launch. */
+int idf_attn_f32_split_ok(int B, int N, int D, int terms);
+int idf_attn_f32_split_fwd(const float* qkv, float* o, float* lse, int B, int N, int D, float scale, int terms, void* stream);
+int idf_attn_f32_split_bwd(const float* qkv, const float* dO, const float* lse, const float* o, float* dqkv, int B, int N, int D,
+                           float scale, int terms, void* stream);
+
 /* The proj conv folded into V (round 4): (P V) Wp^T = P (V Wp^T), so with Wv' = Wp Wv and b' = Wp bv + bp (the rows of P sum to one:
  * a bias on V' passes through the product unchanged) the block is y = x + P V' -- no proj launch, no proj data gradient, no proj weight
  * gradient.  idf_attn_fold_batched: Wv' [C][C] and (bq | bk | b') [3C] of every attention block of a network in one launch -- table

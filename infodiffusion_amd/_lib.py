@@ -146,6 +146,9 @@ SIGNATURES = {
     'idf_attn_f32_ok': ([_i, _i, _i], C.c_int),
     'idf_attn_f32_fwd': ([_p, _p, _p, _i, _i, _i, _f, _p], C.c_int),
     'idf_attn_f32_bwd': ([_p, _p, _p, _p, _p, _i, _i, _i, _f, _p], C.c_int),
+    'idf_attn_f32_split_ok': ([_i, _i, _i, _i], C.c_int),
+    'idf_attn_f32_split_fwd': ([_p, _p, _p, _i, _i, _i, _f, _i, _p], C.c_int),
+    'idf_attn_f32_split_bwd': ([_p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p], C.c_int),
     'idf_prep_u8': ([_p, _p, _p, _i, _i, _i, _i, _p], C.c_int),
     'idf_qsample': ([_p, _p, _p, _p, _p, _p, _p, _l, _l, _i, _p], C.c_int),
     'idf_gather_rows': ([_p, _p, _p, _i, _i, _p], C.c_int),

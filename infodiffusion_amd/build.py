@@ -17,7 +17,8 @@ EXTRA = {'idf_elementwise.hip': ['-ffp-contract=off'],
          'idf_wgrad_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_wgrad_split.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
          'idf_conv_resample_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
-         'idf_attn_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+         'idf_attn_f32.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+         'idf_attn_f32_split.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def needs_build():

@@ -152,17 +152,19 @@ def f32_halo_ok(B, H, W, Cin, Cout):
     return bool(_lib.load().idf_conv3x3_f32_ok(B, H, W, Cin, Cout))
 
 
-# the fp32 stride-1 3x3 convs (forward and data gradient, idf_conv3x3_f32_split) and the stride-1 weight gradients (3x3 and 1x1,
-# idf_conv_wgrad_f32_split) on split-bf16 MFMA operands: 0 exact (default), 3 = bf16x3 (fp32-grade), 2 = bf16x2 (3 * 2^-18 per product).
-# Bias gradients, the gather-mode (stride-2, up-sampling, few-channel) weight gradients, resample convs, 1x1 forward convs and
-# attention stay exact.
+# the fp32 stride-1 3x3 convs (forward and data gradient, idf_conv3x3_f32_split), the stride-1 weight gradients (3x3 and 1x1,
+# idf_conv_wgrad_f32_split) and the attention (forward and backward, idf_attn_f32_split_fwd / _bwd) on split-bf16 MFMA operands:
+# 0 exact (default), 3 = bf16x3 (fp32-grade), 2 = bf16x2 (3 * 2^-18 per product).
+# Bias gradients, the gather-mode (stride-2, up-sampling, few-channel) weight gradients, resample convs, 1x1 forward convs, the
+# softmax arithmetic inside the attention and the one-launch attention block stay exact.
 _F32_SPLIT = 0
 _F32_MFMA_MODES = {'exact': 0, 'bf16x3': 3, 'bf16x2': 2}
 
 
 def set_f32_mfma(mode):
-    """Arithmetic of the fp32 stride-1 3x3 convs (forward, data gradient) and of the stride-1 3x3 / 1x1 weight gradients: 'exact'
-    (fp32 MFMA, the default), 'bf16x3' or 'bf16x2' (split-bf16 MFMA).  Everything else in the fp32 path stays exact in every mode.
+    """Arithmetic of the fp32 stride-1 3x3 convs (forward, data gradient), of the stride-1 3x3 / 1x1 weight gradients and of the
+    attention's matrix products (forward, backward): 'exact' (fp32 MFMA, the default), 'bf16x3' or 'bf16x2' (split-bf16 MFMA).
+    Everything else in the fp32 path, the attention's softmax included, stays exact in every mode.
     Set it before a model is captured: a captured graph keeps the launches it recorded."""
     global _F32_SPLIT
     if mode not in _F32_MFMA_MODES:
@@ -251,6 +253,16 @@ _F32_ATTN = True
 @functools.lru_cache(maxsize=None)
 def f32_attn_ok(B, N, C):
     return bool(_lib.load().idf_attn_f32_ok(B, N, C))
+
+
+# in the split modes (_F32_SPLIT != 0) the fp32 attention runs its matrix products on split-bf16 operands (idf_attn_f32_split_fwd /
+# _bwd), tried before the exact fused route and the bgemm route; False: the routing of 'exact' mode
+_F32_SPLIT_ATTN = True
+
+
+@functools.lru_cache(maxsize=None)
+def f32_attn_split_ok(B, N, C, terms):
+    return bool(_lib.load().idf_attn_f32_split_ok(B, N, C, terms))
 
 
 def conv_raw(x, w_fwd, bias, residual, sc, sh, seed, salt, p_drop, mode, taps, act, Cout, out_hw_=None, want_stats=False):
@@ -955,7 +967,7 @@ def switch_state():
     every graph that is kept across calls (sampling._graphed)."""
     g = globals()
     return tuple(g[k] if not isinstance(g[k], list) else tuple(g[k]) for k in (
-        '_FEWC', '_F32_HALO', '_F32_SPLIT', '_F32_SPLIT_WGRAD', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
+        '_FEWC', '_F32_HALO', '_F32_SPLIT', '_F32_SPLIT_WGRAD', '_F32_SPLIT_ATTN', '_F32_WGRAD', '_F32_WGRAD_GATHER', '_F32_ATTN', '_GN_FUSE', '_WR', '_WR_MAXB', '_RS', '_RS_FWD_ALL', '_RS_SHARED', '_SC_FUSE', '_RB_SMALL', '_RB_SMALL_MAXB',
         '_RB_WFRAG', '_UPCONV', '_ATTN_FOLD', '_ATTN_BLOCK', '_ATTN_BLOCK_MINB', '_TEMB_FUSED'))
 
 
@@ -2068,6 +2080,14 @@ class _Attention(torch.autograd.Function):
         C, N = C3 // 3, H * W
         dev, dt = qkv.device, qkv.dtype
         ctx.fused = bool(_lib.load().idf_attn_fused_ok(N, C, _dt(qkv)))
+        ctx.f32_split = (_F32_SPLIT if dt == torch.float32 and qkv.is_cuda and pre is None and _F32_SPLIT and _F32_SPLIT_ATTN
+                         and f32_attn_split_ok(B, N, C, _F32_SPLIT) else 0)
+        if ctx.f32_split:   # the same streaming launch on split-bf16 MFMA operands
+            o = empty_nhwc(B, C, H, W, dt, dev)
+            lse = torch.empty((B, N), dtype=torch.float32, device=dev)
+            call('idf_attn_f32_split_fwd', _p(qkv), _p(o), _p(lse), B, N, C, float(int(C) ** (-0.5)), ctx.f32_split, _st())
+            ctx.save_for_backward(qkv, lse, o)
+            return o
         ctx.f32 = dt == torch.float32 and qkv.is_cuda and pre is None and _F32_ATTN and f32_attn_ok(B, N, C)
         if ctx.f32:         # one launch, K and V streamed through LDS, scores and probabilities in registers
             o = empty_nhwc(B, C, H, W, dt, dev)
@@ -2102,6 +2122,10 @@ class _Attention(torch.autograd.Function):
         do = _nhwc(do.to(qkv.dtype))
         scale = float(int(C) ** (-0.5))
         dqkv = torch.empty_like(qkv, memory_format=CL)
+        if ctx.f32_split:                    # P is the row logsumexp of idf_attn_f32_split_fwd, same mode as the forward
+            call('idf_attn_f32_split_bwd', _p(qkv), _p(do), _p(P), _p(ctx.saved_tensors[2]), _p(dqkv), B, N, C, scale,
+                 ctx.f32_split, _st())
+            return dqkv, None
         if ctx.f32:                          # P is the row logsumexp of idf_attn_f32_fwd
             call('idf_attn_f32_bwd', _p(qkv), _p(do), _p(P), _p(ctx.saved_tensors[2]), _p(dqkv), B, N, C, scale, _st())
             return dqkv, None

@@ -72,9 +72,9 @@ def parse_args(argv=None):
                         'the reference, epsilon-hat within 2e-2: DESIGN.md section 2) or fp32 (exact-f32 MFMA; within '
                         '1e-4 of the reference)')
     p.add_argument('--f32_mfma', default='exact', choices=['exact', 'bf16x3', 'bf16x2'],
-                   help='arithmetic of the fp32 stride-1 3x3 convs (forward and data gradient) and of the stride-1 3x3 / 1x1 weight '
-                        'gradients with --act_dtype fp32: exact fp32 MFMA, or split-bf16 MFMA operands -- bf16x3 (fp32-grade) / bf16x2 '
-                        '(3 * 2^-18 per product); everything else stays exact')
+                   help='arithmetic of the fp32 stride-1 3x3 convs (forward and data gradient), of the stride-1 3x3 / 1x1 weight '
+                        'gradients and of the attention (forward and backward) with --act_dtype fp32: exact fp32 MFMA, or split-bf16 '
+                        'MFMA operands -- bf16x3 (fp32-grade) / bf16x2 (3 * 2^-18 per product); everything else stays exact')
     p.add_argument('--steps_per_epoch', type=int, default=100)
     p.add_argument('--graph', type=int, default=1, help='replay the train step from a captured hipGraph')
     args = p.parse_args(argv)
